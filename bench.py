@@ -18,6 +18,8 @@ Prints ONE JSON line on rank 0.  At N = 1 the line also carries "extra_configs":
 kernel, VALU-issue roofline), configs[3] (CNN), the logits variant, Dist-M, the same model through the generic fused kernel
 and the reference's documented 12 KB model family (docs/documentation.md:169-183) — each timed on the same resident image set
 and checked against the oracle on a sample.
+--dump-outputs DIR: after the timed steps, what the last one computed (class ids; logits with --logits) as DIR/<name>.npy, a fixed
+seeded sample above 64 MB (dump_outputs), so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -326,9 +328,9 @@ def load_model_through_the_text_parser(b, name, header=None):
     """The product's model path is exporter TEXT -> run-time parser -> GPU.  Sources, in this order: --header; the header the
     REFERENCE'S OWN EXPORTER wrote in this repository (tests/golden/headers/, committed: the ternary 96-96-96 models and the
     documented 12 KB family); the REFERENCE'S OWN FILE (BitNetMCU_model_fc.h, BitNetMCU_model_cnn.h, mcu/*.h), a byte-identical
-    copy staged by oracle/build_oracle.py under tests/golden/_ref_headers/ where /root/reference exists and shipped to the GPU box
-    (sha256 in its MANIFEST.json).  Whatever was parsed must equal the committed weight blob (bitnetmcu_amd/zoo/<name>.bnm).  Only
-    a tree that has neither (a fresh clone that never saw the reference) re-emits the blob as text with the package's own writer."""
+    copy committed under tests/golden/_ref_headers/ (oracle/build_oracle.py --stage-headers; sha256 in its MANIFEST.json).  Whatever
+    was parsed must equal the committed weight blob (bitnetmcu_amd/zoo/<name>.bnm).  A zoo model with neither header re-emits the
+    blob as text with the package's own writer."""
     if header:
         return b.Model.from_header(header), "exporter-written header file " + header + " through the run-time parser"
     blob_model = b.Model.from_zoo(name)
@@ -343,7 +345,7 @@ def load_model_through_the_text_parser(b, name, header=None):
             sha = hashlib.sha256(open(path, "rb").read()).hexdigest()
             if sha != man["sha256"]:
                 raise RuntimeError(f"{path}: not the bytes that were staged from {man['origin']}")
-            what = f"the reference's own {man['origin'][len('/root/reference/'):]}, byte-identical staged copy, sha256 {sha[:16]}"
+            what = f"the reference's own {man['origin']}, byte-identical staged copy, sha256 {sha[:16]}"
         model = b.Model.from_header(path)
         if model.to_blob() != blob_model.to_blob():
             raise RuntimeError(f"{name}: {path} does not parse to the committed blob")
@@ -376,6 +378,39 @@ def timed_steps(torch, step, steps, warmup, barrier=None):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     return elapsed, [evs[k].elapsed_time(evs[k + 1]) for k in range(steps)]
+
+
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: every file of one run together
+DUMP_MAX_ROWS = 1 << 22
+DUMP_SEED = 20240421
+
+
+def dump_outputs(out_dir, np, torch, cls, logits, first, rank, world):
+    """--dump-outputs DIR: what the timed call handed its caller in the LAST timed step - the class ids of this rank's images
+    (and the logits with --logits) - as DIR/class_ids.npy (float32: ids are small integers, exact) and DIR/logits.npy (float64:
+    every int32 exact).  Outputs above this rank's share of the budget (and above DUMP_MAX_ROWS rows) are a sample: one row drawn
+    with a fixed seed from each of equal slices of the images, so the same arguments dump the same rows in every run;
+    DIR/image_index.npy (float64) holds the global image index of every row written.  Ranks > 1 add _rank<r> to the names."""
+    n = cls.shape[0]
+    row_bytes = 4 + 8 + (8 * logits.shape[1] if logits is not None else 0)
+    rows = min(n, DUMP_MAX_ROWS, (DUMP_LIMIT_BYTES // world - 4096) // row_bytes)
+    if rows == n:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        k = np.arange(rows + 1, dtype=np.int64)
+        lo = k[:-1] * n // rows
+        width = k[1:] * n // rows - lo
+        idx = lo + (np.random.default_rng(DUMP_SEED).random(rows) * width).astype(np.int64)
+    sel = torch.from_numpy(idx).to(cls.device)
+    arrays = {"class_ids": cls.index_select(0, sel).cpu().numpy().astype(np.float32),
+              "image_index": (idx + first).astype(np.float64)}
+    if logits is not None:
+        arrays["logits"] = logits.index_select(0, sel).cpu().numpy().astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
+    print(f"# dump-outputs: {rows} of {n} rows ({', '.join(arrays)}) in {out_dir}", file=sys.stderr, flush=True)
 
 
 def relaunch_with_ranks(a):
@@ -428,9 +463,14 @@ def main():
     ap.add_argument("--full-json", default=os.path.join(REPO, "bench_full.json"), help="where rank 0 writes the full record (every row in detail)")
     ap.add_argument("--header", default=None, help="load the model from this exporter-written BitNetMCU_model.h (text parser) "
                                                   "instead of bitnetmcu_amd/zoo/<model>.bnm")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (class ids, logits with --logits) as DIR/<name>.npy: "
+                         "at most 64 MB, a fixed seeded sample of larger outputs")
     a = ap.parse_args()
     if a.gpus < 1:
         sys.exit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        sys.exit("--steps must be >= 1 and --warmup >= 0")
     if a.ranks_share_device and a.dist_backend != "gloo":
         sys.exit("--ranks-share-device needs --dist-backend gloo (RCCL wants one device per rank)")
 
@@ -522,6 +562,8 @@ def main():
         td.all_gather(every, mine)
         per_rank = [[float(x[0].item()), float(x[1].item())] for x in every]
         elapsed = max(x[0] for x in per_rank)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, np, torch, cls, logits, first, rank, world)
 
     # ---- outside the timed region: verification ----------------------------------------------------------
     verified = None

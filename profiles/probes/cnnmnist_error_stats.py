@@ -1,7 +1,8 @@
 import os, sys, numpy as np, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo")); sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tests"))
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
 from bitnetmcu_amd import qat
-GM = np.load(os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tests/golden/qat_fc_model.npz"))
+GM = np.load(os.path.join(REPO, "tests/golden/qat_fc_model.npz"))
 m = qat.CNNMNIST(96, 64, 0, cnn_width=64, QuantType="4bitsym").cuda()
 layers = [x for x in list(m.model) + [m.classifier] if hasattr(x, "weight_quant")]
 with torch.no_grad():

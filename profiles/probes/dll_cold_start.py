@@ -1,6 +1,7 @@
 import time, sys, os
 t00 = time.perf_counter()
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, REPO)
 import numpy as np
 import bitnetmcu_amd as b
 t0 = time.perf_counter()

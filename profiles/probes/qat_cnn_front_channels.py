@@ -1,5 +1,7 @@
 import sys, json, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+import os
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, REPO)
 from bitnetmcu_amd import qat
 for C in (16, 32, 48, 64, 128):
     torch.manual_seed(C)

@@ -1,5 +1,5 @@
 import os, sys, subprocess, json
-repo = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+repo = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for rows in (1000000, 10000000):
     res = {"0": [], "1": []}
     for rep in range(4):

@@ -143,6 +143,44 @@ def test_bench_line_is_short_enough_for_the_driver():
         bench.compact_line(big)
 
 
+def test_dump_outputs_writes_the_outputs_or_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: a small output is written whole and exactly (class ids float32, logits float64); a large one is
+    the same seeded sample every time, sorted and distinct global image indices, 64 MB at most over all files."""
+    import numpy as np
+    import torch
+    import bench
+    rng = np.random.default_rng(3)
+    cls = torch.from_numpy(rng.integers(0, 47, size=1000, dtype=np.int32))
+    lg = torch.from_numpy(rng.integers(-2**31, 2**31, size=(1000, 47), dtype=np.int64).astype(np.int32))
+    bench.dump_outputs(str(tmp_path / "small"), np, torch, cls, lg, 500, 0, 1)
+    got = {f: np.load(tmp_path / "small" / f) for f in ("class_ids.npy", "logits.npy", "image_index.npy")}
+    assert got["class_ids.npy"].dtype == np.float32 and np.array_equal(got["class_ids.npy"], cls.numpy())
+    assert got["logits.npy"].dtype == np.float64 and np.array_equal(got["logits.npy"], lg.numpy())
+    assert np.array_equal(got["image_index.npy"], np.arange(500, 1500))
+    # above the row cap (class ids only) and above the byte budget (47 logits per row): samples
+    n = 9_000_000
+    big = torch.from_numpy((np.arange(n, dtype=np.int32) % 10))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), np, torch, big, None, 7, 0, 1)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["class_ids.npy", "image_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    idx = np.load(tmp_path / "a" / "image_index.npy").astype(np.int64) - 7
+    assert len(idx) == bench.DUMP_MAX_ROWS and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(np.load(tmp_path / "a" / "class_ids.npy"), (idx % 10).astype(np.float32))
+    n = 200_000
+    cls = torch.from_numpy(rng.integers(0, 47, size=n, dtype=np.int32))
+    lg = torch.from_numpy(rng.integers(-2**31, 2**31, size=(n, 47), dtype=np.int64).astype(np.int32))
+    bench.dump_outputs(str(tmp_path / "c"), np, torch, cls, lg, 0, 0, 1)
+    assert sum(os.path.getsize(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")) <= 64 << 20
+    idx = np.load(tmp_path / "c" / "image_index.npy").astype(np.int64)
+    assert 100_000 < len(idx) < n and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert np.array_equal(np.load(tmp_path / "c" / "class_ids.npy"), cls.numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "c" / "logits.npy"), lg.numpy()[idx])
+
+
 def test_build_rebuilds_when_the_command_changes(tmp_path, capsys):
     """an object is reused only when the files it includes are older than it AND it was built by the same command
     (flags, architecture, compiler version - the stamp beside it); a changed flag or a foreign stamp recompiles."""

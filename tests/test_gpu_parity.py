@@ -826,6 +826,26 @@ def _check_bench_stdout(stdout):
     return c
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(gpu_ok, orc, tmp_path):
+    """bench.py --dump-outputs DIR: the class ids and logits the timed call returned, every image of a small run, equal the oracle's;
+    --steps sets the number of timed steps the line reports."""
+    import json
+    import subprocess
+    import sys
+    d = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(util.REPO, "bench.py"), "--images", "20000", "--steps", "2", "--warmup", "1",
+                          "--logits", "--no-cpu", "--no-extra", "--full-json", str(tmp_path / "full.json"), "--dump-outputs", str(d)],
+                         capture_output=True, text=True, timeout=900)
+    c = _check_bench_stdout(out.stdout)
+    assert c["steps"] == 2 and c["warmup"] == 1 and c["verified_vs_oracle"] is True
+    assert np.array_equal(np.load(d / "image_index.npy"), np.arange(20000))
+    want_cls, want_logits = util.OracleModel(util.load_golden_model("fc_4bitsym_64"), orc).infer(synth.images(0, 20000, DIST_U), logits=True)
+    cls, logits = np.load(d / "class_ids.npy"), np.load(d / "logits.npy")
+    assert cls.dtype == np.float32 and logits.dtype == np.float64
+    assert np.array_equal(cls, want_cls) and np.array_equal(logits, want_logits)
+    assert json.load(open(tmp_path / "full.json"))["steps"] == 2
+
+
 def test_bench_json_contract(gpu_ok, tmp_path):
     """bench.py on a small N: ONE short JSON line with the contract's keys as the last stdout line, every detail in the full record
     (--full-json), verified against the oracle."""
