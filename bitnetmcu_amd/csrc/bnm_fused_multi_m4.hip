@@ -1,0 +1,3 @@
+// Several FC models over one image stream, tile class 4 (layers of up to 128 outputs): see bnm_fused_multi_kernel.hpp.
+#include "bnm_fused_multi_kernel.hpp"
+BNM_MULTI_LAUNCHER(bnmk_multi_launch_m4, 4)

@@ -1,0 +1,3 @@
+// Several FC models over one image stream, tile class 6 (layers of up to 192 outputs): see bnm_fused_multi_kernel.hpp.
+#include "bnm_fused_multi_kernel.hpp"
+BNM_MULTI_LAUNCHER(bnmk_multi_launch_m6, 6)

@@ -105,6 +105,37 @@ hipError_t bnmk_fused_generic(const BnmGenericDesc &d, bool dbl, int tiles, int 
                               const void *d_frags, uint32_t *d_cls, int32_t *d_logits, uint32_t *d_counter, uint32_t batch,
                               hipStream_t s);
 
+// ---- several FC models over one image stream (bnm_fused_multi.hip): the generic kernel's formulation, the fragment images of a
+// GROUP of models staged into LDS together, every 32-image tile read once and run through all of them -----------------------
+constexpr uint32_t BNM_MULTI_MAX_MODELS = 16;
+struct BnmMultiModel {       // one model of a group (the generic kernel's descriptor, offsets relative to the GROUP's image)
+    uint32_t M[4];           // 32-row output tiles per FC layer (exact); M[3] == 0 for 3-layer models
+    uint32_t frag_off[4];    // byte offset of each layer's fragments inside the group's fragment image
+    uint32_t sp;             // 1, or 2 with FP1.3.0's second weight plane
+    uint32_t dbl;            // hidden-layer weight fragments doubled (bnm_ctx shape.dbl)
+    uint32_t n_classes;
+    uint32_t pad_;
+    uint32_t *cls;           // [n] class ids of the call (set per call)
+    int32_t *logits;         // [n][n_classes] or nullptr (set per call)
+};
+struct BnmMultiArgs {        // passed to the kernel by value
+    const int8_t *images;    // [n][256]
+    uint64_t n;
+    const void *frags;       // the group's fragment image: the models' generic images back to back
+    uint32_t w_bytes;        // its size (a multiple of 1 KiB)
+    uint32_t g;              // models in the group, 1 .. BNM_MULTI_MAX_MODELS
+    uint32_t *counter;       // the launch's counter block (all zero on entry, left all zero)
+    uint32_t batch;          // set by the launcher: tiles per take | counter words << 16
+    uint32_t pad_;
+    BnmMultiModel model[BNM_MULTI_MAX_MODELS];
+};
+// tile class of a group: the largest mmax among its models' generic descriptors (2, 4, 6 or 8)
+uint32_t bnmk_multi_class(uint32_t mmax);
+// waves per CU a launch of a group with this fragment image size and tile class gets (0: it does not fit)
+uint32_t bnmk_multi_waves(uint32_t w_bytes, uint32_t mclass);
+// a.images / n / frags / w_bytes / g / counter / model[0 .. g) set by the caller
+hipError_t bnmk_fused_multi(uint32_t mclass, int grid_blocks, BnmMultiArgs &a, hipStream_t s);
+
 // ---- fused float-input whole-model FC kernel (bnm_fused_f32.hip): float32 [n][256] -> input quantisation -> the FC stack, one
 // kernel, on the generic kernel's descriptor and fragment image.  Serves 256-value rows (KT0 == 8) of the 2- and 4-tile classes
 // whose weights leave LDS for at least one wave per SIMD.  groups: 8-image groups in flight per wave (0 = default; 2 or 4).

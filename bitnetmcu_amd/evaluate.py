@@ -22,7 +22,7 @@ differ in rare cases): this evaluator is the C engine.  argmax agrees wherever t
 import numpy as np
 
 from . import _lib as L
-from .model import Model, Context
+from .model import Model, Context, MultiContext
 
 # Lk_bitperweight ids written by the exporter (exportquant.py:105-177)
 _QUANT_ID = {"Binary": 1, "2bitsym": 2, "4bitsym": 4, "4bit": 12, "8bit": 16, "FP130": 20, "NF4": 36, "Ternary": 64}
@@ -228,3 +228,31 @@ def accuracy(ctx, images_float, labels, batch=1 << 20):
     pred = predict(ctx, images_float, batch)
     labels = np.asarray(labels)
     return float((pred == labels).mean()), pred
+
+
+def compare(models, images_float, labels=None, device=-1, batch=1 << 20):
+    """Several models on the same images in one pass per LDS-sized group (MultiContext): the generalisation of the reference's
+    "Mismatches between engines" count (test_inference.py:152-175) to k models.
+    models: a list of Model objects, or a MultiContext.  images_float: [n,256] (or [n,16,16]) float32, quantised once on the GPU.
+    Returns {"accuracy": [k floats] (labels given) or None, "disagree": int64 [k, k] - images on which models i and j predict
+    different classes, counted on the GPU from the ids -, "pred": uint32 [k, n]}."""
+    import torch
+    mc = models if isinstance(models, MultiContext) else MultiContext(models, device)
+    x = np.ascontiguousarray(images_float, dtype=np.float32).reshape(-1, 256)
+    n, k = len(x), mc.k
+    dev = torch.device("cuda", device if device >= 0 else torch.cuda.current_device())
+    pred = np.empty((k, n), np.uint32)
+    disagree = torch.zeros((k, k), dtype=torch.int64, device=dev)
+    correct = torch.zeros(k, dtype=torch.int64, device=dev)
+    lab = None if labels is None else np.asarray(labels).reshape(-1)
+    for s in range(0, n, batch):
+        xb = torch.from_numpy(x[s:s + batch]).to(dev)
+        cls = torch.empty((k, len(xb)), dtype=torch.int32, device=dev)
+        mc.infer_float_device(xb, cls)
+        disagree += (cls[:, None, :] != cls[None, :, :]).sum(dim=2)
+        if lab is not None:
+            lb = torch.from_numpy(lab[s:s + batch].astype(np.int64)).to(dev)
+            correct += (cls.long() == lb[None, :]).sum(dim=1)
+        pred[:, s:s + batch] = cls.cpu().numpy().astype(np.uint32)
+    acc = None if lab is None else [float(c) / n if n else 0.0 for c in correct.cpu().tolist()]
+    return {"accuracy": acc, "disagree": disagree.cpu().numpy(), "pred": pred}

@@ -281,3 +281,94 @@ class Context:
         L.check(self._lib, self._lib.bnm_quantize_input_device(x.data_ptr(), n, out.data_ptr(), s.cuda_stream),
                 "bnm_quantize_input_device")
         return out
+
+
+class MultiContext:
+    """Several FC models on one GPU, run over the same images in one pass (bnm_multi): the images are read once per group of
+    models whose weights fit the LDS together, not once per model.  `models`: 1 .. 16 Model objects (FC, 256-byte inputs; the
+    same model may appear twice).  Row m of every result belongs to models[m]."""
+
+    def __init__(self, models, device=-1):
+        models = list(models)
+        if not models:
+            raise ValueError("MultiContext needs at least one model")
+        self._lib = models[0]._lib
+        self.models = models
+        arr = (C.c_void_p * len(models))(*[m._h.value if isinstance(m._h, C.c_void_p) else m._h for m in models])
+        h = C.c_void_p()
+        L.check(self._lib, self._lib.bnm_multi_create(C.cast(arr, C.c_void_p), len(models), device, C.byref(h)), "bnm_multi_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bnm_multi_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def k(self):
+        return len(self.models)
+
+    @property
+    def groups(self):
+        """Passes over the images one call makes: launches of the multi-model kernel plus models that run alone."""
+        return self._lib.bnm_multi_groups(self._h)
+
+    def _logit_ptrs(self, logits):
+        if logits is None:
+            return None
+        assert len(logits) == self.k
+        return (C.c_void_p * self.k)(*[t.data_ptr() for t in logits])
+
+    def infer(self, images, logits=False):
+        """images: int8 array [n,256] (or [n,16,16]).  Returns class ids uint32 [k, n] and, if asked, a list of k int32 arrays
+        [n, num_classes of model m]."""
+        x = np.ascontiguousarray(images, dtype=np.int8).reshape(-1, 256)
+        n = x.shape[0]
+        cls = np.empty((self.k, n), np.uint32)
+        lg = [np.empty((n, m.num_classes), np.int32) for m in self.models] if logits else None
+        ptrs = (C.c_void_p * self.k)(*[a.ctypes.data for a in lg]) if logits else None
+        L.check(self._lib, self._lib.bnm_multi_infer_host(self._h, x.ctypes.data, n, cls.ctypes.data, ptrs), "bnm_multi_infer_host")
+        return (cls, lg) if logits else cls
+
+    def infer_device(self, images, cls, logits=None, stream=None):
+        """Asynchronous launch on torch's current stream (or `stream`).  images: torch.int8 [n,256] cuda tensor; cls: int32 cuda
+        tensor [k, n] (contiguous); logits: None or a list of k int32 cuda tensors [n, num_classes of model m]."""
+        import torch
+        n = images.shape[0]
+        assert images.is_cuda and images.is_contiguous() and images.dtype == torch.int8
+        assert cls.is_cuda and cls.is_contiguous() and cls.element_size() == 4 and cls.numel() >= self.k * n
+        if logits is not None:
+            assert all(t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() >= n * m.num_classes
+                       for t, m in zip(logits, self.models))
+        s = stream if stream is not None else torch.cuda.current_stream(images.device)
+        L.check(self._lib, self._lib.bnm_multi_infer_device(self._h, images.data_ptr(), n, cls.data_ptr(), self._logit_ptrs(logits),
+                                                            s.cuda_stream), "bnm_multi_infer_device")
+        return cls
+
+    def infer_float_device(self, x, cls, logits=None, stream=None):
+        """float32 cuda tensor [n,256] -> class ids [k, n]: quantised once (as Context.quantize_device) for all k models."""
+        import torch
+        n = x.numel() // 256
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
+        assert cls.is_cuda and cls.is_contiguous() and cls.element_size() == 4 and cls.numel() >= self.k * n
+        if logits is not None:
+            assert all(t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() >= n * m.num_classes
+                       for t, m in zip(logits, self.models))
+        s = stream if stream is not None else torch.cuda.current_stream(x.device)
+        L.check(self._lib, self._lib.bnm_multi_infer_float_device(self._h, x.data_ptr(), n, cls.data_ptr(), self._logit_ptrs(logits),
+                                                                  s.cuda_stream), "bnm_multi_infer_float_device")
+        return cls
+
+    @property
+    def float_nonfinite(self):
+        """Images, over all float calls of this object so far, that held a NaN or an infinity (each classified as the all-zero
+        image).  Waits for this object's float calls only (bnm_multi_float_nonfinite)."""
+        v = C.c_uint64(0)
+        L.check(self._lib, self._lib.bnm_multi_float_nonfinite(self._h, C.byref(v)), "bnm_multi_float_nonfinite")
+        return int(v.value)

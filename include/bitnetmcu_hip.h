@@ -282,6 +282,33 @@ BNM_API int bnm_ctx_set_float_mode(bnm_ctx *c, int mode, int groups);
 BNM_API int bnm_ctx_float_nonfinite(bnm_ctx *c, uint64_t *count);
 BNM_API int bnm_ctx_float_fused(const bnm_ctx *c);      /* 1: float calls of this context run one kernel now (CNN: those that take the one-kernel form); 0: two kernels */
 
+/* ---- several FC models over one image batch ---------------------------------------------------
+ * A bnm_multi holds 1 .. 16 FC models (256-byte inputs, a fused MFMA path; they may differ in depth, widths, codecs and class
+ * counts, and the same model may appear twice) on one GPU.  One call runs all of them over the same images: the planner groups the
+ * models, in the caller's order, into groups whose fragment images fit the LDS together, and a launch per group reads each image
+ * ONCE and runs it through every model of the group (fused_fc_multi_kernel).  A model whose fragment image alone exceeds the budget
+ * runs through its own single-model context.  Results are those of each model's single-model calls, however the models are grouped.
+ * CNN models and inputs other than 256 bytes: BNM_EUNSUPPORTED.  k outside 1 .. 16, null or misaligned pointers: BNM_EINVAL; the
+ * argument checks come before any device call.  n == 0 is a no-op.  Any number of calls may be in flight on any streams (each
+ * stream gets its own counter block and scratch); HIP graph capture of these calls is NOT supported. */
+typedef struct bnm_multi bnm_multi;
+BNM_API int bnm_multi_create(const bnm_model *const *models, uint32_t k, int device, bnm_multi **out);
+BNM_API void bnm_multi_destroy(bnm_multi *mc);
+/* passes over the images a call makes: launches of the multi-model kernel + models run alone */
+BNM_API int bnm_multi_groups(const bnm_multi *mc);
+/* d_images int8 [n][256] (16-byte aligned), d_cls uint32 [k][n] (row m: model m's class ids), d_logits: NULL, or k device pointers
+ * (a host array), pointer m to int32 [n][classes of model m].  Asynchronous on `stream`. */
+BNM_API int bnm_multi_infer_device(bnm_multi *mc, const int8_t *d_images, uint64_t n, uint32_t *d_cls, int32_t *const *d_logits,
+                                   void *stream);
+/* float32 [n][256] images, quantised ONCE (as bnm_quantize_input_device; non-finite images zeroed and counted) for all k models */
+BNM_API int bnm_multi_infer_float_device(bnm_multi *mc, const float *d_x, uint64_t n, uint32_t *d_cls, int32_t *const *d_logits,
+                                         void *stream);
+/* the same with host pointers (cls [k][n], logits NULL or k host pointers); synchronous */
+BNM_API int bnm_multi_infer_host(bnm_multi *mc, const int8_t *images, uint64_t n, uint32_t *cls, int32_t *const *logits);
+/* images, over all float calls of this object so far, that held a NaN or an infinity.  Waits for this object's last float call on
+ * each stream it used - not for the whole device. */
+BNM_API int bnm_multi_float_nonfinite(bnm_multi *mc, uint64_t *count);
+
 /* ---- QAT forward op ------------------------------------------------------
  * The forward pass of the reference's training layer BitLinear (BitNetMCU.py:198-235):
  *   y = F.linear(act_quant(Normalize(x)), weight_quant(w))        x [n][d], w [k][d], y [n][k], float32
