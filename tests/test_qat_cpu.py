@@ -263,3 +263,59 @@ def test_front_backward_from_saved_planes_equals_autograd_through_the_whole_fron
     for a, b_ in zip([gx] + gws, want):
         assert a.shape == b_.shape and (a - b_).abs().max() <= 2e-5 * b_.abs().max().clamp(min=1e-30)
     assert qat.cnn_front_backward(x.detach(), *planes, ws, ss, qts, g, need_gx=False)[0] is None
+
+
+# ---- the float64 yardstick of the GPU tests (tests/qat_f64.py) against the reference module's own outputs ----------------------
+@pytest.mark.parametrize("tag", sorted(MODEL_CONFIGS))
+def test_f64_reference_chain_equals_the_reference_module(tag):
+    """qat_f64's FC chain from x with the reference's levels: every row whose quantised products are all more than TIE from a tie in
+    every layer matches the reference module's float32 logits and hidden activations within qat_f64's tight bound - the float64
+    evaluation IS the reference's formula before any GPU test leans on it.  (The all-zero row is NaN in both.)"""
+    import qat_f64
+    qt, nt = MODEL_CONFIGS[tag]
+    x, ws, ss, _ = model_case(tag)
+    levels, scales = [], []
+    for w, s in zip(ws, ss):
+        u, sc, lo, hi = qat_f64.reference_levels(w, s, qt)
+        assert torch.equal(u, torch.from_numpy(GM[f"{tag}/w_int{len(levels)}"]))
+        # the kernel-level check accepts the reference's own w_int / w_scale, unchanged
+        _, _, changed = qat_f64.kernel_levels(u / sc.float(), w, s, qt)
+        assert not changed.any()
+        levels.append(u.double())
+        scales.append(sc)
+    outs, clean = qat_f64.fc_chain(x, levels, scales, nt)
+    assert clean.float().mean() >= 0.25, float(clean.float().mean())
+    ref_l, ref_h = torch.from_numpy(GM[f"{tag}/logits"]).double(), torch.from_numpy(GM[f"{tag}/hidden"]).double()
+    hid = torch.cat(outs[:-1], dim=1)
+    if nt != "LayerNorm":
+        assert torch.isnan(outs[-1][5]).all()
+    for got, want, what in ((outs[-1], ref_l, "logits"), (hid, ref_h, "hidden")):
+        g, w = got[clean], want[clean]
+        row_max = w.abs().amax(dim=1, keepdim=True)
+        assert bool(((g - w).abs() <= qat_f64.FC_TIGHT * row_max).all()), (tag, what, float(((g - w).abs() / row_max).max()))
+    # layer by layer on the reference's own hidden activations: within the derived bound on EVERY row
+    offs = np.concatenate([[0], np.cumsum([w.shape[0] for w in ws[:-1]])])
+    xin = x
+    for l in range(len(ws)):
+        y, tie, step = qat_f64.fc_layer(xin, levels[l], scales[l], nt)
+        last = l + 1 == len(ws)
+        got = ref_l if last else ref_h[:, offs[l]:offs[l + 1]]
+        qat_f64.within(got, y if last else torch.relu(y), step, qat_f64.FC_TIGHT, (tag, l))
+        xin = got.float()
+
+
+def test_f64_reference_front_equals_the_reference_module():
+    """qat_f64's convolution front from the images with the reference's levels: every feature whose quantised inputs, through all three
+    layers, are all more than TIE from a tie (qat_f64.front_chain) equals the reference module's within qat_f64's tight bound (of the
+    image's largest feature)."""
+    import qat_f64
+    ws = [torch.from_numpy(GM[f"cnn/w{l}"]) for l in range(3)]
+    ss = [torch.from_numpy(GM[f"cnn/s{l}"]) for l in range(3)]
+    taps = qat_f64.cnn_taps(ws, ss, ["8bit"] * 3)
+    y1, y2, y3, feats, clean = qat_f64.front_chain(torch.from_numpy(GM["cnn/x"]), taps)
+    assert clean.float().mean() >= 0.25, float(clean.float().mean())
+    ref = torch.from_numpy(GM["cnn/features"]).double()
+    row_max = ref.abs().amax(dim=1, keepdim=True).expand_as(ref)
+    err = (feats - ref).abs()[clean]
+    assert bool((err <= qat_f64.CNN_TIGHT * row_max[clean]).all()), float((err / row_max[clean]).max())
+    assert y1.shape == (45, 64, 14, 14) and y2.shape == (45, 64, 12, 12) and y3.shape == (45, 64, 4, 4)
