@@ -147,7 +147,7 @@ __global__ __launch_bounds__(64 * QAT_WAVES) void qat_bitlinear_fwd_kernel(
             }
             den = sqrtf(wave_sum(b) / (float)d + 1e-5f);
         }
-        float mx = 0.0f;
+        float mx = 0.0f, has_nan = 0.0f;
         for (uint32_t c = lane; c < d; c += 64) {
             float v = qr[c];
             if (nt == BNM_QAT_NORM_BATCHNORM) v = __fdiv_rn(__fsub_rn(v, bn_mean[c]), bn_den[c]);
@@ -155,21 +155,29 @@ __global__ __launch_bounds__(64 * QAT_WAVES) void qat_bitlinear_fwd_kernel(
             else if (nt != BNM_QAT_NORM_NONE) v = __fdiv_rn(v, den);
             qr[c] = v;
             mx = fmaxf(mx, fabsf(v));
+            if (v != v) has_nan = 1.0f;
         }
         if (qt == BNM_QAT_NONE) {
             if (lane == 0) xs[r] = 1.0f;
             continue;
         }
         mx = wave_max(mx);
-        const float sc = __fdiv_rn(127.0f, fmaxf(mx, 1e-5f));
+        has_nan = wave_max(has_nan);
+        // Non-finite rows as the reference's torch code: its max|x| propagates a NaN (fmaxf drops it), and so does the clamp at 1e-5,
+        // so a NaN (an all-zero row under RMS / Lin is 0 / 0) makes the scale NaN; an infinity makes it 127 / inf = 0 and that
+        // value's product inf * 0 NaN.  Either way x_int / x_scale, and the row's y, are NaN throughout: xs[] carries the NaN into
+        // the outputs, x_int keeps the NaN products (fminf / fmaxf would clamp them to -128) and the int8 tile gets 0 for them.
+        const float sc = has_nan != 0.0f ? __builtin_nanf("") : __fdiv_rn(127.0f, fmaxf(mx, 1e-5f));
+        const bool nan_row = has_nan != 0.0f || mx == __builtin_inff();
         for (uint32_t c = lane; c < d; c += 64) {
-            float v = fminf(fmaxf(rintf(__fmul_rn(qr[c], sc)), -128.0f), 127.0f);
+            const float p = __fmul_rn(qr[c], sc);
+            const float v = p != p ? p : fminf(fmaxf(rintf(p), -128.0f), 127.0f);
             qr[c] = v;
-            if (u8) q8[r * rs8 + c] = (int8_t)(int)v;
+            if (u8) q8[r * rs8 + c] = p != p ? (int8_t)0 : (int8_t)(int)v;
             if (x_int_out) x_int_out[row * d + c] = v;
         }
         if (lane == 0) {
-            xs[r] = sc;
+            xs[r] = nan_row ? __builtin_nanf("") : sc;
             if (x_scale_out) x_scale_out[row] = sc;
         }
     }
@@ -260,18 +268,22 @@ __global__ __launch_bounds__(256) void qat_bitconv2d_fwd_kernel(const float *__r
         }
         for (uint32_t r = wave; r < h; r += 4u) {
             float *pr = plane + (r + pad) * wp + pad;
-            float mx = 0.0f;
+            float mx = 0.0f, has_nan = 0.0f;
             for (uint32_t cc = lane; cc < wd; cc += 64u) {
                 float v = xp[r * wd + cc];
                 if (nt == BNM_QAT_NORM_RMS) v = __fdiv_rn(v, den);
                 pr[cc] = v;
                 mx = fmaxf(mx, fabsf(v));
+                if (v != v) has_nan = 1.0f;
             }
             if (qt == BNM_QAT_NONE) continue;
             mx = wave_max(mx);
+            // an image row holding a NaN (an all-zero plane under RMS is 0 / 0) or an infinity is NaN throughout after
+            // activation_quant, as in the reference (see qat_bitlinear_fwd_kernel); the padding around it stays 0
+            const bool nan_row = wave_max(has_nan) != 0.0f || mx == __builtin_inff();
             const float sc = __fdiv_rn(127.0f, fmaxf(mx, 1e-5f));
             for (uint32_t cc = lane; cc < wd; cc += 64u)
-                pr[cc] = __fdiv_rn(fminf(fmaxf(rintf(__fmul_rn(pr[cc], sc)), -128.0f), 127.0f), sc);
+                pr[cc] = nan_row ? __builtin_nanf("") : __fdiv_rn(fminf(fmaxf(rintf(__fmul_rn(pr[cc], sc)), -128.0f), 127.0f), sc);
         }
     }
     __syncthreads();
@@ -334,7 +346,7 @@ hipError_t bnmk_qat_bitlinear_forward(const float *x, uint64_t n, uint32_t d, co
     float *stats = w_scale + kpad;
     float *bn_mean = stats + 4, *bn_den = bn_mean + d;
     const uint32_t d8 = (d + 31u) & ~31u;
-    // int8 matrix path for the types that allow it - unless the extra byte tile no longer fits beside the float tile (d > ~900)
+    // int8 matrix path for the types that allow it - unless the extra byte tile no longer fits beside the float tile in 160 KiB (d >= 1019)
     const bool i8_fits = ((size_t)QAT_ROWS * (dpad + 1u) + QAT_ROWS) * sizeof(float) + (size_t)QAT_ROWS * (d8 + 16u) <= 160u * 1024u;
     int8_t *u8 = (qat_i8_factor(qt) && i8_fits) ? (int8_t *)(bn_den + d) : nullptr;
     hipError_t e = hipMemsetAsync(workspace, 0, ((size_t)dpad * kpad + kpad + 4u) * sizeof(float), st);

@@ -1,6 +1,7 @@
 """The reference's QAT forward formulas evaluated in float64, with every quantised value's distance from a rounding tie: the yardstick
-the floating-point QAT kernels (csrc/bnm_qat_model.hip, csrc/bnm_qat_cnn.hip) are held to, shared by their GPU tests and pinned to
-the reference module's own fixtures on CPU by tests/test_qat_cpu.py.  A plain helper module (torch tensors on any device).
+the floating-point QAT kernels (csrc/bnm_qat.hip, csrc/bnm_qat_model.hip, csrc/bnm_qat_cnn.hip) are held to, shared by their GPU tests
+and pinned to the reference module's own fixtures on CPU by tests/test_qat_cpu.py.  A plain helper module (torch tensors on any
+device).
 
 The formulas are qat.normalize / activation_quant / weight_quant / ste_formula / ste_conv_formula (BitNetMCU.py:119-177, 214-235,
 284-305), rounded to float32 wherever the reference rounds - Normalize's denominator and quotient, activation_quant's scale and the
@@ -104,7 +105,10 @@ def act_quant(xn):
 
 
 def normalize(x, nt):
-    """BitLinear.Normalize (BitNetMCU.py:237-262) on float32 values held in float64: denominator and quotient rounded to float32"""
+    """BitLinear.Normalize (BitNetMCU.py:237-262) on float32 values held in float64: denominator and quotient rounded to float32.
+    LayerNorm / BatchNorm: the row's / the batch's (per feature, dimension 0) statistics, the mean rounded to float32 before the
+    float32 subtraction.  A NaN
+    or an infinity reaches the result as it does in the reference's torch code (an all-zero row under RMS / Lin is 0 / 0 = NaN)."""
     if nt == "RMS":
         den = f32(torch.sqrt((x * x).mean(dim=1, keepdim=True)))
     elif nt == "Lin":
@@ -112,21 +116,32 @@ def normalize(x, nt):
     elif nt == "LayerNorm":
         mean = x.mean(dim=1, keepdim=True)
         den = f32(torch.sqrt(((x - mean) ** 2).mean(dim=1, keepdim=True) + 1e-5))
-        x = f32(x - mean)
+        x = f32(x - f32(mean))     # (the float32 mean: where the row's spread is far below its mean, its rounding is what counts)
+    elif nt == "BatchNorm":
+        mean = x.mean(dim=0, keepdim=True)
+        den = f32(torch.sqrt(((x - mean) ** 2).mean(dim=0, keepdim=True) + 1e-5))
+        x = f32(x - f32(mean))
+    elif nt == "None":
+        return x
     else:
         raise AssertionError(nt)
     return f32(x / den)
 
 
 # ---- a BitLinear layer ---------------------------------------------------------------------------------------------------------
-def fc_layer(x_in, levels, w_scale, nt):
+def fc_layer(x_in, levels, w_scale, nt, quant=True):
     """One BitLinear layer (BitNetMCU.py:214-235) from a float32 input [n, d] (any d: Normalize averages over the d values):
-    levels [k, d] and w_scale (scalar or [k, 1]) float64 -> (y [n, k], tie [n, d], step [n, k]): y exact given the rounded
-    quantities, tie the distance of every quantised product from a rounding tie, step the sum over the row's near-tie inputs of one
-    quantisation step's effect on each output, |level| / (x_scale w_scale)."""
+    levels [k, d] and w_scale (scalar, PerTensor, or [k, 1], PerOutput) float64 -> (y [n, k], tie [n, d], step [n, k]): y exact
+    given the rounded quantities, tie the distance of every quantised product from a rounding tie, step the sum over the row's
+    near-tie inputs of one quantisation step's effect on each output, |level| / (x_scale w_scale).  quant=False: QuantType 'None'
+    (F.linear of the normalised input and the float32 weights `levels`; no tie, no step)."""
     x = x_in.double()
     with torch.no_grad():
-        xi, xs, tie = act_quant(normalize(x, nt))
+        xn = normalize(x, nt)
+        if not quant:
+            return xn @ levels.t(), torch.full_like(xn, float("inf")), torch.zeros(x.shape[0], levels.shape[0], dtype=x.dtype,
+                                                                                    device=x.device)
+        xi, xs, tie = act_quant(xn)
         ws = w_scale.reshape(1, -1) if w_scale.numel() > 1 else w_scale.reshape(1, 1)
         y = (xi @ levels.t()) / xs / ws
         near = (tie <= TIE).double()
@@ -180,11 +195,13 @@ def cnn_taps(ws, ss, qts, kernel_taps=None):
     return out
 
 
-def within(got, want, step, tight, what, cap=None, floor_rows=False):
-    """Per-output check of `got` against `want` (float64, rows = dimension 0): NaN exactly where `want` is NaN; elsewhere
-    |got - want| <= tight x (the row's largest |want| + step) + step - the kernel rounds at the size of what it computes, which is up
-    to a step away from `want`.  cap: every row's largest error within cap of its largest |want|
-    (floor_rows: of max(that, a tenth of the median row maximum) - a row of one or two outputs can sit near zero)."""
+def within(got, want, step, tight, what, cap=None, floor_rows=False, extra=None):
+    """Per-output check of `got` against `want` (float64, rows = dimension 0): NaN exactly where `want` is NaN, an infinity exactly
+    where `want` has the same one; elsewhere |got - want| <= tight x (the row's largest finite |want| + step) + step + extra - the
+    kernel rounds at the size of what it computes, which is up to a step away from `want`; `extra` (optional, per output): a bound on
+    the kernel's own float32 summation error where its terms do not sum exactly.  cap: every row's largest error within cap of its
+    largest |want| (floor_rows: of max(that, a tenth of the median row maximum) - a row of one or two outputs can sit near zero).
+    -> the largest ratio of error to allowance."""
     if want.shape[0] == 0:
         return 0.0
     got = got.double().reshape(want.shape[0], -1)
@@ -192,23 +209,74 @@ def within(got, want, step, tight, what, cap=None, floor_rows=False):
     step = step.reshape(want.shape[0], -1)
     nan_w, nan_g = torch.isnan(want), torch.isnan(got)
     assert torch.equal(nan_w, nan_g), (what, "NaN pattern", int((nan_w != nan_g).sum()))
-    rows = ~nan_w.any(dim=1)
-    g, w, s = got[rows], want[rows], step[rows]
-    if g.shape[0] == 0:
+    inf_w = torch.isinf(want)
+    assert torch.equal(inf_w, torch.isinf(got)) and torch.equal(got[inf_w], want[inf_w]), (what, "infinities")
+    fin = ~(nan_w | inf_w)      # (a row with a NaN is NaN throughout in a linear layer; a convolution plane may keep finite outputs)
+    if not bool(fin.any()):
         return 0.0
-    row_max = w.abs().amax(dim=1, keepdim=True)
-    err = (g - w).abs()
+    zero = torch.zeros_like(want)
+    row_max = torch.where(fin, want, zero).abs().amax(dim=1, keepdim=True)
+    err = torch.where(fin, (got - want).abs(), zero)
+    s = torch.where(fin, step, zero)
     allowed = tight * (row_max + s) + s      # (a flipped step is |level| / (x_scale w_scale) in the kernel's own float32 scales)
+    if extra is not None:
+        allowed = allowed + torch.where(fin, extra.reshape(want.shape), zero)
     ratio = float((err / allowed.clamp(min=1e-300)).max())
     bad = err > allowed
     assert not bool(bad.any()), (what, "outside the derived bound", int(bad.any(dim=1).sum()), float((err - allowed).max()), ratio)
     if cap is not None:
+        live = fin.any(dim=1, keepdim=True)
         scale = row_max
         if floor_rows:
-            scale = torch.maximum(row_max, 0.1 * row_max.median())
+            scale = torch.maximum(row_max, 0.1 * row_max[live].median())
         rel = err.amax(dim=1, keepdim=True) / scale.clamp(min=1e-30)
-        assert bool((rel <= cap).all()), (what, "above the cap", float(rel.max()))
+        assert bool((rel[live] <= cap).all()), (what, "above the cap", float(rel[live].max()))
     return ratio
+
+
+# ---- a general BitConv2d --------------------------------------------------------------------------------------------------------
+def conv2d_layer(x, taps, stride=1, pad=0, groups=1, nt="None", quant=True):
+    """BitConv2d (BitNetMCU.py:284-322) of float32 planes x [n, cin, h, w] held in float64, with taps [cout, cin / groups, kh, kw]
+    float64 = level / w_scale (quant=False, QuantType 'None': the float32 weights), any groups, square stride, symmetric zero padding:
+    Normalize ('RMS' over each plane, :306-308, or 'None'), activation_quant per image row BEFORE padding, zero padding after it,
+    then the convolution as im2col (F.unfold) and a float64 product (MIOpen has no float64 convolution)
+    -> (y [n, cout, ho, wo], step [same]: one quantisation step per near-tie input times |tap|, absum [same]: sum |x_q tap|)."""
+    a = x.double()
+    cout, cig, kh, kw = taps.shape
+    with torch.no_grad():
+        if nt == "RMS":
+            a = f32(a / f32(torch.sqrt((a * a).mean(dim=(2, 3), keepdim=True))))
+        elif nt != "None":
+            raise AssertionError(nt)
+        if quant:
+            xi, xs, tie = act_quant(a)
+            xq, near = xi / xs, (tie <= TIE).double() / xs
+        else:
+            xq, near = a, torch.zeros_like(a)
+        n, cin, h, wd = a.shape
+        ho, wo = (h + 2 * pad - kh) // stride + 1, (wd + 2 * pad - kw) // stride + 1
+        t = taps.double().reshape(groups, cout // groups, cig * kh * kw)
+
+        def conv(v, tt):
+            cols = F.unfold(F.pad(v, (pad, pad, pad, pad)), (kh, kw), stride=stride).reshape(n, groups, cig * kh * kw, ho * wo)
+            return torch.einsum("gok,ngkl->ngol", tt, cols).reshape(n, cout, ho, wo)
+
+        y = conv(xq, t)
+        step = conv(near, t.abs())
+        absum = conv(xq.abs(), t.abs())
+    return y, step, absum
+
+
+def conv_allowance(absum, taps):
+    """The kernel's own float32 error on top of CNN_TIGHT: it keeps x_int / x_scale and level / w_scale as rounded floats and
+    accumulates d = cig kh kw products with fmaf, so (d + 2) roundings of at most 2^-24 of sum |x_q tap| per output"""
+    d = taps.shape[1] * taps.shape[2] * taps.shape[3]
+    return (d + 2) * 2.0 ** -24 * absum
+
+
+def plane_rows(t):
+    """[n, c, ho, wo] -> [n c, ho wo]: one row per (image, channel) plane, the unit `within` scales CNN_TIGHT by"""
+    return t.reshape(t.shape[0] * t.shape[1], -1)
 
 
 # ---- whole forward passes --------------------------------------------------------------------------------------------------------
@@ -258,3 +326,110 @@ def front_chain(x, taps):
         else:
             a, dirty = relu_pool(y), _any2x2(dirty)
     return ys[0], ys[1], ys[2], a.flatten(1), ~dirty.flatten(1)
+
+
+# ---- the per-layer GPU op (csrc/bnm_qat.hip) judged output by output ---------------------------------------------------------------
+# QuantTypes whose products x_int * level sum exactly in float32 (integers or half-integers, |sum| <= 2^24): the kernel's y is its exact
+# sum divided by its two scales, two float32 roundings
+EXACT_SUM = ("Binary", "BinarySym", "Ternary", "2bitsym", "4bitsym", "5bitsym", "8bit", "FP130")
+U = 2.0 ** -24          # the unit roundoff of float32
+XSCALE_ULPS = 8         # x_scale: the kernel sums the row's squares / absolute values in another order than the reference
+
+
+def _ulp32(v):
+    """the spacing of float32 at |v| (float64 tensor in, float64 tensor out)"""
+    a = v.abs().float()
+    return (torch.nextafter(a, torch.full_like(a, float("inf"))) - a).double()
+
+
+def workspace_levels(device, d, k):
+    """the levels uT [dpad][kpad] -> [k, d] and w_scale [k] the last per-layer call of shape (d, k) on this stream used (float32)"""
+    ws = qat._workspaces[(device.index, torch.cuda.current_stream(device).cuda_stream, d, k)]
+    dpad, kpad = (d + 1) & ~1, (k + 31) & ~31
+    return ws[:dpad * kpad].reshape(dpad, kpad)[:d, :k].t().contiguous(), ws[dpad * kpad:dpad * kpad + k].clone()
+
+
+def _check_weights(w, s, qt, wdq, u_ws, wsc_ws):
+    """the kernel's levels (workspace) and w_int / w_scale (return_w_deq, what the backward consumes) per weight -> (levels, scale) f64"""
+    if qt == "None":
+        assert torch.equal(wdq, w) and torch.equal(u_ws, w.reshape(u_ws.shape)), "QuantType None: the weights themselves"
+        return w.double(), torch.ones((), dtype=torch.float64, device=w.device)
+    lev, scale, _ = kernel_levels(wdq, w, s, qt)
+    lev2 = lev.reshape(u_ws.shape)
+    assert torch.equal(u_ws.double(), lev2), (qt, "workspace levels differ from w_int / w_scale's", int((u_ws.double() != lev2).sum()))
+    want_sc = scale.reshape(-1).expand(u_ws.shape[0])
+    tol = 2 * _ulp32(want_sc) if qt == "Ternary" else 0.0      # (Ternary: mean|w| summed in another order)
+    assert bool(((wsc_ws.double() - want_sc).abs() <= tol).all()), (qt, "w_scale")
+    deq = (u_ws.double() / wsc_ws.double()[:, None]).float()       # (53 >= 2 x 24 + 2 bits: the float32 quotient, correctly rounded)
+    assert torch.equal(wdq.reshape(deq.shape), deq), (qt, "w_deq is not level / w_scale in float32", int((wdq.reshape(deq.shape) != deq).sum()))
+    return lev, scale
+
+
+def check_bitlinear(x, w, s, qt, nt, what=""):
+    """qat.bitlinear_forward on x [n, d], w [k, d], s (scalar or [k]) against the float64 layer, every element:
+      * weights: the workspace's levels and w_scale and return_w_deq (= level / w_scale in float32), per weight (`kernel_levels`);
+      * activations: x_int equals the float64 act_quant value, or lies +-1 from it where that value is within TIE of a tie; x_scale
+        within XSCALE_ULPS float32 ulps; NaN exactly where the float64 evaluation has it;
+      * self-consistency: y against the exact value of the kernel's OWN x_int, x_scale, levels and w_scale - within 4 U of it for the
+        exactly summed types (an exact 0 gives 0), plus (d + 1) U sum |x_int level| / (x_scale w_scale) for '4bit' / 'NF4';
+      * end to end: y within FC_TIGHT of the float64 layer (with the kernel's levels) on every row, plus a step per near-tie input.
+    -> the largest ratio of error to allowance of the end-to-end check"""
+    n, d = x.shape
+    k = w.shape[0]
+    quant = qt != "None"
+    out = qat.bitlinear_forward(x, w, s, qt, nt, return_int=quant, return_w_deq=True)
+    y, wdq = out[0], out[-1]
+    torch.cuda.synchronize()
+    u_ws, wsc_ws = workspace_levels(x.device, d, k)
+    lev, scale = _check_weights(w, s, qt, wdq, u_ws, wsc_ws)
+    lev = lev.reshape(k, d)
+    y64, tie, step = fc_layer(x, lev, scale, nt, quant)
+    y = y.double()
+    if not quant:
+        xn = normalize(x.double(), nt)
+        extra = (d + 8) * U * (xn.abs() @ lev.abs().t())        # (the kernel's normalised values carry a few roundings of their own)
+        return within(y, y64, step, FC_TIGHT, (what, qt, nt), extra=extra)
+    xi, xs = out[1].double(), out[2].double()
+    xi64, xs64, tie = act_quant(normalize(x.double(), nt))
+    xs64 = xs64.reshape(-1)
+    assert torch.equal(torch.isnan(xs), torch.isnan(xs64)), (what, qt, nt, "x_scale NaN pattern")
+    assert torch.equal(torch.isnan(xi), torch.isnan(xi64)), (what, qt, nt, "x_int NaN pattern")
+    f = ~torch.isnan(xs64)
+    assert bool(((xs[f] - xs64[f]).abs() <= XSCALE_ULPS * _ulp32(xs64[f])).all()), (what, qt, nt, "x_scale",
+                                                                                    float(((xs[f] - xs64[f]).abs() / _ulp32(xs64[f])).max()))
+    fi = ~torch.isnan(xi64)
+    dx = (xi - xi64).abs()
+    assert bool((dx[fi & (tie > TIE)] == 0).all()) and bool((dx[fi] <= 1).all()), (what, qt, nt, "x_int", int((dx[fi] != 0).sum()))
+    # self-consistency on the rows the kernel computed finitely
+    rows = torch.isfinite(xs) & (xs != 0) & torch.isfinite(xi).all(dim=1)
+    ws = wsc_ws.double()[None, :] if scale.numel() > 1 else wsc_ws.double()[:1][None, :]
+    exact = (xi[rows] @ u_ws.double().t()) / xs[rows, None] / ws
+    allowed = 4 * U * exact.abs()
+    if qt not in EXACT_SUM:
+        allowed = allowed + (d + 1) * U * (xi[rows].abs() @ u_ws.double().abs().t()) / xs[rows, None] / ws
+    err = (y[rows] - exact).abs()
+    assert bool((err <= allowed).all()), (what, qt, nt, "y against the kernel's own operands", int((err > allowed).sum()),
+                                          float((err / allowed.clamp(min=1e-300)).max()))
+    ws64 = scale.reshape(1, -1) if scale.numel() > 1 else scale.reshape(1, 1)
+    extra = None if qt in EXACT_SUM else (d + 1) * U * (xi64.abs() @ lev.abs().t()) / xs64[:, None] / ws64
+    return within(y, y64, step, FC_TIGHT, (what, qt, nt), extra=extra)
+
+
+def check_bitconv2d(x, w, s, qt, nt, stride=1, pad=0, groups=1, what=""):
+    """qat.bitconv2d_forward against the float64 convolution with the kernel's own levels (workspace, `kernel_levels`), every output,
+    per (image, channel) plane: CNN_TIGHT of the plane's largest |y| + (d + 2) U sum |x_q tap| + one step per near-tie input;
+    NaN exactly where the float64 evaluation has it.  -> the largest ratio of error to allowance"""
+    y = qat.bitconv2d_forward(x, w, s, qt, nt, stride, (pad, pad), groups)
+    torch.cuda.synchronize()
+    cout, cig, kh, kw = w.shape
+    u_ws, wsc_ws = workspace_levels(x.device, cig * kh * kw, cout)
+    if qt == "None":
+        assert torch.equal(u_ws, w.reshape(cout, -1))
+        taps = w.double()
+    else:
+        lev, scale, _ = kernel_levels((u_ws.double() / wsc_ws.double()[:, None]).float(), w, s, qt)
+        taps = lev / scale
+    y64, step, absum = conv2d_layer(x, taps, stride, pad, groups, nt, qt != "None")
+    assert y.shape == y64.shape, (what, tuple(y.shape), tuple(y64.shape))
+    return within(plane_rows(y), plane_rows(y64), plane_rows(step), CNN_TIGHT, (what, qt, nt),
+                  extra=plane_rows(conv_allowance(absum, taps)))

@@ -319,3 +319,112 @@ def test_f64_reference_front_equals_the_reference_module():
     err = (feats - ref).abs()[clean]
     assert bool((err <= qat_f64.CNN_TIGHT * row_max[clean]).all()), float((err / row_max[clean]).max())
     assert y1.shape == (45, 64, 14, 14) and y2.shape == (45, 64, 12, 12) and y3.shape == (45, 64, 4, 4)
+
+
+# ---- the float64 yardstick of the per-layer GPU tests (tests/test_gpu_qat.py, tests/test_gpu_qat_layers.py) -----------------------
+def _f64_linear_cases():
+    return ([("a", qt, nt) for qt in QUANTS for nt in NORMS] + [("odd", qt, "RMS") for qt in ("4bitsym", "8bit")]
+            + [("perout", qt, "RMS") for qt in ("4bitsym", "2bitsym")])
+
+
+@pytest.mark.parametrize("tag,qt,nt", _f64_linear_cases())
+def test_f64_linear_layer_equals_the_reference_module(tag, qt, nt):
+    """qat_f64.fc_layer with the reference's levels (PerTensor or PerOutput w_scale) against the reference module's y: every row whose
+    quantised products are all more than TIE from a tie within FC_TIGHT of its largest output, every row within the derived bound;
+    qat_f64.normalize / act_quant against the module's x_norm, x_int and x_scale where the fixture holds them."""
+    import qat_f64
+    x, w, s = t(f"{tag}/x"), t(f"{tag}/w"), t(f"{tag}/{qt}/s")
+    u, sc, _, _ = qat_f64.reference_levels(w, s, qt)
+    assert torch.equal(u, t(f"{tag}/{qt}/w_int")) and torch.equal(sc.float().reshape(-1), t(f"{tag}/{qt}/w_scale"))
+    y, tie, step = qat_f64.fc_layer(x, u.double(), sc, nt)
+    ref = t(f"{tag}/{qt}/{nt}/y").double()
+    clean = (tie > qat_f64.TIE).all(dim=1)
+    assert clean.float().mean() >= 0.25, float(clean.float().mean())
+    row_max = ref.abs().amax(dim=1, keepdim=True)
+    assert bool(((y - ref).abs()[clean] <= qat_f64.FC_TIGHT * row_max[clean]).all()), (tag, qt, nt)
+    qat_f64.within(ref, y, step, qat_f64.FC_TIGHT, (tag, qt, nt))
+    if f"{tag}/{nt}/x_int" in G:
+        xn = qat_f64.normalize(x.double(), nt)
+        ref_xn = t(f"{tag}/{nt}/x_norm").double()
+        # (x - mean cancels in BatchNorm / LayerNorm: the module's float32 mean and variance move small values by many of their
+        # own ulps - a few ulps of the row's largest value, which the x_int / x_scale checks below hold to account)
+        assert bool(((xn - ref_xn).abs() <= 2.0 ** -20 * ref_xn.abs().amax(dim=1, keepdim=True)).all()), (tag, nt)
+        xi, xs, tie = qat_f64.act_quant(xn)
+        ref_xs = t(f"{tag}/{nt}/x_scale").double()
+        assert bool(((xs.reshape(-1) - ref_xs).abs() <= 4 * torch.from_numpy(np.spacing(t(f"{tag}/{nt}/x_scale").numpy())).double()).all())
+        diff = (xi - t(f"{tag}/{nt}/x_int").double()).abs()
+        assert bool((diff[tie > qat_f64.TIE] == 0).all()) and bool((diff <= 1).all()), (tag, nt)
+
+
+def test_f64_linear_layer_none_and_batchnorm_match_the_module_formula():
+    """QuantType 'None' (F.linear of the normalised input) and NormType 'None' / 'BatchNorm' - no reference fixture holds them: the
+    float64 layer against qat.ste_formula (pinned to the reference above) evaluated in float64, every row, FC_TIGHT"""
+    import qat_f64
+    x, w = t("a/x"), t("a/w")
+    for nt in NORMS + ["None"]:
+        want = torch.nn.functional.linear(qat.normalize(x.double(), nt), w.double())
+        y, _, step = qat_f64.fc_layer(x, w.double(), torch.ones(()), nt, quant=False)
+        assert not step.any()
+        qat_f64.within(y, want, step, 1e-6, ("None", nt))
+    u, sc, _, _ = qat_f64.reference_levels(w, t("a/4bitsym/s"), "4bitsym")
+    y, _, step = qat_f64.fc_layer(x, u.double(), sc, "None")
+    want = qat.ste_formula(x.double(), w.double(), t("a/4bitsym/s").double()[0], "4bitsym", "None")
+    qat_f64.within(want, y, step, qat_f64.FC_TIGHT, ("4bitsym", "None"))
+
+
+def test_f64_normalize_propagates_nan_as_the_reference_does():
+    """an all-zero row is 0 / 0 = NaN under RMS and Lin, finite under LayerNorm (its epsilon); a row holding +-inf or NaN is NaN
+    after activation_quant for every NormType (NormType 'None' with an infinity: scale 127 / inf = 0, x_int / x_scale = 0 / 0);
+    BatchNorm: a column holding an infinity makes every row NaN, a constant column is 0 - all as qat.normalize / activation_quant"""
+    import qat_f64
+    x = torch.randn(6, 37)
+    x[1] = 0.0
+    x[2, 5] = float("inf")
+    x[3, 0] = float("-inf")
+    x[4, 9] = float("nan")
+    for nt in ("RMS", "Lin", "LayerNorm", "None", "BatchNorm"):
+        xb = x if nt != "BatchNorm" else x[[0, 1, 5]]
+        xn = qat_f64.normalize(xb.double(), nt)
+        ref_xn = qat.normalize(xb, nt)
+        assert torch.equal(torch.isnan(xn), torch.isnan(ref_xn)), nt
+        xi, xs, _ = qat_f64.act_quant(xn)
+        ref_xi, ref_xs = qat.activation_quant(ref_xn)
+        assert torch.equal(torch.isnan(xi), torch.isnan(ref_xi)) and torch.equal(torch.isnan(xs), torch.isnan(ref_xs)), nt
+        assert torch.equal(torch.isnan(xi / xs), torch.isnan(ref_xi / ref_xs)), nt
+    xi, xs, _ = qat_f64.act_quant(qat_f64.normalize(x.double(), "None"))
+    assert float(xs[2]) == 0.0 and torch.isnan(xi[2, 5]) and not torch.isnan(xi[2, :5]).any()
+    xb = x[[0, 2, 5]]
+    assert torch.isnan(qat_f64.normalize(xb.double(), "BatchNorm")).all(dim=0).any()
+    xc = torch.randn(4, 8)
+    xc[:, 3] = 0.75
+    assert not qat_f64.normalize(xc.double(), "BatchNorm")[:, 3].any()
+
+
+def _f64_conv_cases():
+    cases = [(G, tag, 3, 1, pad, groups, qt, nt) for tag, (cin, cout, groups, qt, nt, pad) in
+             [("conv1", (1, 16, 1, "8bit", "None", 0)), ("convdw", (16, 16, 16, "8bit", "None", 0)),
+              ("convdw_rms", (8, 16, 8, "4bitsym", "RMS", 1)), ("conv1_tern", (1, 12, 1, "Ternary", "RMS", 0))]]
+    gc = np.load(os.path.join(GOLDEN, "qat_bitconv2d_general.npz"))
+    return cases + [(gc, tag, ks, stride, pad, groups, qt, nt) for tag, ks, stride, pad, groups, qt, nt in GENERAL_CONV]
+
+
+@pytest.mark.parametrize("case", _f64_conv_cases(), ids=lambda c: c[1])
+def test_f64_conv_layer_equals_the_reference_module(case):
+    """qat_f64.conv2d_layer with the reference's levels against the reference module's y, per (image, channel) plane: outputs no
+    near-tie input reaches within CNN_TIGHT of the plane's largest |y| plus the float32 summation allowance, every output within that
+    plus one step per near-tie input"""
+    import qat_f64
+    g, tag, ks, stride, pad, groups, qt, nt = case
+    x, w, s = (torch.from_numpy(g[f"{tag}/{k}"]) for k in ("x", "w", "s"))
+    u, sc, _, _ = qat_f64.reference_levels(w, s, qt)
+    taps = u.double() / sc
+    y, step, absum = qat_f64.conv2d_layer(x, taps, stride, pad, groups, nt)
+    ref = torch.from_numpy(g[f"{tag}/y"]).double()
+    assert y.shape == ref.shape
+    extra = qat_f64.conv_allowance(absum, taps)
+    rows = qat_f64.plane_rows
+    err, row_max = rows(y - ref).abs(), rows(ref).abs().amax(dim=1, keepdim=True)
+    clean = rows(step) == 0
+    assert clean.float().mean() >= 0.5, float(clean.float().mean())
+    assert bool((err <= qat_f64.CNN_TIGHT * row_max + rows(extra))[clean].all()), tag
+    qat_f64.within(rows(ref), rows(y), rows(step), qat_f64.CNN_TIGHT, tag, extra=rows(extra))
