@@ -87,6 +87,10 @@ PROTOTYPES = {
     "bnm_multi_infer_float_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "bnm_multi_infer_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp]),
     "bnm_multi_float_nonfinite": (C.c_int, [_vp, _u64p]),
+    "bnm_model_profile_words": (C.c_uint64, [_vp, _u32p, _u32p]),
+    "bnm_infer_device_profiled": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "bnm_infer_float_device_profiled": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "bnm_ctx_set_profile_mode": (C.c_int, [_vp, C.c_int]),
     "bnm_qat_workspace_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
     "bnm_qat_bitconv2d_forward_device": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32,
                                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_int, C.c_int, _vp, _vp,

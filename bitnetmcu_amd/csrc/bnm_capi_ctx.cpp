@@ -116,9 +116,9 @@ void evict_other_streams(bnm_ctx *c, hipStream_t keep) {
     if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); return; }
     for (auto it = c->scratch.begin(); it != c->scratch.end();) {
         bool frozen = false;
-        for (DevBuf *b : {&it->second.act_a, &it->second.act_b, &it->second.out32, &it->second.cnn_feat, &it->second.q8}) frozen = frozen || b->frozen;
+        for (DevBuf *b : it->second.bufs()) frozen = frozen || b->frozen;
         if (it->first == keep || frozen) { ++it; continue; }      // (a captured graph may still replay on a frozen entry's buffers)
-        for (DevBuf *b : {&it->second.act_a, &it->second.act_b, &it->second.out32, &it->second.cnn_feat, &it->second.q8}) b->release();
+        for (DevBuf *b : it->second.bufs()) b->release();
         it = c->scratch.erase(it);
     }
     for (auto it = c->work_of.begin(); it != c->work_of.end();) {
@@ -166,7 +166,7 @@ bnm_ctx::StreamScratch &stream_scratch(bnm_ctx *c, hipStream_t s_real) {
         it = c->scratch.emplace(s, bnm_ctx::StreamScratch{}).first;
     }
     if (capturing)      // what a captured launch touches stays where it is (DevBuf::frozen)
-        for (DevBuf *b : {&it->second.act_a, &it->second.act_b, &it->second.out32, &it->second.cnn_feat, &it->second.q8}) b->frozen = true;
+        for (DevBuf *b : it->second.bufs()) b->frozen = true;
     return it->second;
 }
 
@@ -613,10 +613,10 @@ int bnm_ctx_release_stream(bnm_ctx *c, void *stream) {
     auto it = c->scratch.find(s);
     if (it != c->scratch.end()) {
         bool frozen = false;
-        for (DevBuf *b : {&it->second.act_a, &it->second.act_b, &it->second.out32, &it->second.cnn_feat, &it->second.q8}) frozen = frozen || b->frozen;
+        for (DevBuf *b : it->second.bufs()) frozen = frozen || b->frozen;
         if (frozen)
             return fail(BNM_EUNSUPPORTED, "launches captured on this stream reference its scratch buffers: they stay until the context is destroyed");
-        for (DevBuf *b : {&it->second.act_a, &it->second.act_b, &it->second.out32, &it->second.cnn_feat, &it->second.q8}) b->release();
+        for (DevBuf *b : it->second.bufs()) b->release();
         c->scratch.erase(it);
     }
     auto wt = c->work_of.find(s);

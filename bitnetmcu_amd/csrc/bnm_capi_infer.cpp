@@ -147,12 +147,12 @@ int run_ternary(bnm_ctx *c, const int8_t *d_in, uint64_t n, uint32_t *d_cls, int
 namespace bnm_internal {
 
 int infer_device_locked(bnm_ctx *c, const int8_t *d_images, uint64_t n, uint32_t *d_cls, int32_t *d_logits,
-                        int8_t *d_acts_tap, uint32_t tap_stride, hipStream_t s) {
+                        int8_t *d_acts_tap, uint32_t tap_stride, hipStream_t s, int tap_path) {
     if (!n) return BNM_OK;
     if (!d_images || !d_cls) return fail(BNM_EINVAL, "null device pointer");
     if (((uintptr_t)d_images & 15u) != 0) return fail(BNM_EINVAL, "d_images must be 16-byte aligned");
     const uint32_t ncls = c->model.num_classes();
-    const int path = d_acts_tap ? BNM_PATH_LAYERWISE_ALU : c->path;
+    const int path = d_acts_tap ? tap_path : c->path;
     if (c->model.kind == BNM_KIND_FC) {
         c->last_kernel = tail_names(c, path, n);
         if (path == BNM_PATH_FUSED_MFMA) return run_fused(c, d_images, n, d_cls, d_logits, s);

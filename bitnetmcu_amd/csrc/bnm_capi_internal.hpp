@@ -3,6 +3,7 @@
 // is include/bitnetmcu_hip.h.  Host side only - there is NO CPU compute path behind the ABI: if HIP is unusable, the reference-ABI
 // functions abort() and the bnm_* functions return BNM_EHIP.
 #pragma once
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -207,6 +208,7 @@ struct bnm_ctx {
     bool f32_ok = false;
     int float_mode = 0;         // 0: the fused kernel where it exists, else quantise + infer; 1: fused or BNM_EUNSUPPORTED; 2: always two kernels
     int f32_groups = 0;         // 8-image groups in flight per wave of the fused float kernel (0 = default)
+    int profile_mode = 0;       // bnm_ctx_set_profile_mode: 0 fused where it serves, else tap + reduce; 2 always tap + reduce
     // ternary ALU path
     bool tern_ok = false;
     int *tern_stream = nullptr;   // the trits in the streamed kernel's consumption order (bnmk_ternary_stream_build)
@@ -225,6 +227,8 @@ struct bnm_ctx {
     struct StreamScratch {
         DevBuf act_a, act_b, out32, cnn_feat;
         DevBuf q8;      // bnm_infer_float_device: the quantised images of one chunk
+        DevBuf prof;    // bnm_infer_device_profiled: one chunk's activation rows and class ids
+        std::array<DevBuf *, 6> bufs() { return {&act_a, &act_b, &out32, &cnn_feat, &q8, &prof}; }
     };
     std::map<hipStream_t, StreamScratch> scratch;
     DevBuf argmax, stage_img, stage_cls, stage_logits;
@@ -292,8 +296,9 @@ inline bool cnn_one_kernel_call(const bnm_ctx *c, uint64_t n) {
            !small_call && n < (1ull << 31);
 }
 // ---- bnm_capi_infer.cpp ----------------------------------------------------------------------------------------------
-// whole-model launch on device data (c->mu held, the context's device current); d_acts_tap: the parity tap (layer-wise path)
+// whole-model launch on device data (c->mu held, the context's device current); d_acts_tap: the parity tap (layer-wise path;
+// tap_path: BNM_PATH_LAYERWISE_ALU, or BNM_PATH_LAYERWISE_MFMA where every codec is one the C engine decodes)
 int infer_device_locked(bnm_ctx *c, const int8_t *d_images, uint64_t n, uint32_t *d_cls, int32_t *d_logits,
-                        int8_t *d_acts_tap, uint32_t tap_stride, hipStream_t s);
+                        int8_t *d_acts_tap, uint32_t tap_stride, hipStream_t s, int tap_path = BNM_PATH_LAYERWISE_ALU);
 
 }  // namespace bnm_internal

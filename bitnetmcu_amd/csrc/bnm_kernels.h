@@ -100,6 +100,22 @@ bool bnmk_generic_plan(BnmGenericDesc &d, const uint32_t m_real[4]);   // fills 
 int bnmk_generic_tiles(const BnmGenericDesc &d, bool dbl, int tiles, bool logits);
 bool bnmk_generic_supported(const BnmGenericDesc &d, bool dbl);
 uint32_t bnmk_generic_resident_waves(const BnmGenericDesc &d, bool dbl);   // waves per CU of the default launch (0: does not fit)
+// The profiling variant of the generic kernel (bnm_fused_generic_prof.hip): class ids plus the activation-profile counters of the
+// hidden layers, predictions and labels (include/bitnetmcu_hip.h has the layout).  FC models, tile classes 2 and 4, 256-byte rows.
+struct BnmFusedProf {
+    unsigned long long *ctr = nullptr;     // the caller's counters
+    const int32_t *labels = nullptr;       // [n] or nullptr
+    uint32_t n_layers = 0;                 // profiled layers: the hidden layers, 2 or 3
+    uint32_t width[4] = {};
+    uint32_t word[4] = {};                 // counter word of active[l][0]
+    uint32_t pred = 0, tail = 0;           // counter words of pred[0] and `labelled`
+    uint32_t n_classes = 0;
+};
+// waves per workgroup of a profiled launch (0: no instantiation serves the model, or weights + tallies exceed the LDS)
+uint32_t bnmk_fused_generic_prof_waves(const BnmGenericDesc &d, bool dbl);
+// n <= 2^22 per launch (the kernel's 32-bit LDS tallies); counter: as for bnmk_fused_generic
+hipError_t bnmk_fused_generic_prof(const BnmGenericDesc &d, bool dbl, int grid_blocks, const int8_t *d_images, uint64_t n, const void *d_frags,
+                                   uint32_t *d_cls, uint32_t *d_counter, uint32_t batch, const BnmFusedProf &pa, hipStream_t s);
 // d_counter: a counter block of the caller (BNM_WORK_BLOCK_WORDS words, all zero; the kernel leaves it all zero); batch: units per take (0 = default)
 hipError_t bnmk_fused_generic(const BnmGenericDesc &d, bool dbl, int tiles, int grid_blocks, const int8_t *d_images, uint64_t n,
                               const void *d_frags, uint32_t *d_cls, int32_t *d_logits, uint32_t *d_counter, uint32_t batch,
@@ -237,6 +253,23 @@ hipError_t bnmk_diag_pipes(int mode, uint64_t tiles_per_wave, uint32_t *d_out, h
 // ---- input quantisation: float32 [n][256] -> int8 [n][256] (test_inference.py:140-141) --------------
 // nonfinite (optional): += the images that held a NaN or an infinity (they quantise to all zeros)
 hipError_t bnmk_quantize_input(const float *d_x, uint64_t n, int8_t *d_out, unsigned long long *d_nonfinite, hipStream_t s);
+
+// ---- activation profiles (bnm_profile.hip): int8 activation rows + class ids (+ labels) -> profile counters ------------------
+constexpr uint32_t BNM_PROFILE_MAX_LAYERS = 16;
+struct BnmProfileDesc {
+    uint32_t n_layers = 0;                             // profiled layers
+    uint32_t total = 0;                                // their widths summed: profiled columns of a row
+    uint32_t n_classes = 0;
+    uint32_t first[BNM_PROFILE_MAX_LAYERS + 1] = {};   // first profiled column of layer l (first[n_layers] = total)
+    uint32_t width[BNM_PROFILE_MAX_LAYERS] = {};
+    uint32_t col[BNM_PROFILE_MAX_LAYERS] = {};         // byte offset of layer l's activations in an activation row
+    uint64_t word[BNM_PROFILE_MAX_LAYERS] = {};        // counter word of active[l][0]; sum[l] and hist[l] follow
+    uint64_t pred = 0;                                 // counter word of pred[0]; confusion[][] follows
+    uint64_t tail = 0;                                 // counter word of `labelled`; label_out_of_range and images follow
+};
+// acts: [n][stride] int8 activation rows; cls: [n]; labels: [n] or nullptr; counters: added to, never cleared
+hipError_t bnmk_profile_reduce(const int8_t *acts, uint32_t stride, uint64_t n, const uint32_t *cls, const int32_t *labels,
+                               uint64_t *counters, const BnmProfileDesc &d, hipStream_t s);
 
 // ---- QAT forward op (bnm_qat.hip) ---------------------------------------
 size_t bnmk_qat_workspace_bytes(uint32_t d, uint32_t k);

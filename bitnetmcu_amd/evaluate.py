@@ -230,6 +230,20 @@ def accuracy(ctx, images_float, labels, batch=1 << 20):
     return float((pred == labels).mean()), pred
 
 
+def profile(ctx, images_float, labels=None, batch=1 << 20):
+    """Activation profile of a float test set (evaluate.accuracy's counterpart for activations): the images are quantised and
+    classified on the GPU and every int8 activation that feeds another layer is tallied there, with the predictions and - labels
+    given - the confusion matrix.  ctx: a Context, or a Model (a context on the current device is made for the call).
+    Returns a profile.ActivationProfile."""
+    own = isinstance(ctx, Model)
+    c = Context(ctx) if own else ctx
+    try:
+        return c.profile(np.ascontiguousarray(images_float, dtype=np.float32).reshape(-1, 256), labels, batch)
+    finally:
+        if own:
+            c.close()
+
+
 def compare(models, images_float, labels=None, device=-1, batch=1 << 20):
     """Several models on the same images in one pass per LDS-sized group (MultiContext): the generalisation of the reference's
     "Mismatches between engines" count (test_inference.py:152-175) to k models.

@@ -269,6 +269,52 @@ class Context:
         """True when float calls of this context run the one-kernel path now."""
         return self._lib.bnm_ctx_float_fused(self._h) == 1
 
+    # ---- activation profiles (bnm_infer_device_profiled) ----------------------------------------
+    def profile_words(self):
+        """Counter words (uint64) of this model's activation profile: the size of profile_device's `counters`."""
+        from .profile import layout
+        return layout(self.model)[0]
+
+    def set_profile_mode(self, mode=0):
+        """0: a fused profiling kernel where one serves the model, else tap + reduce; 1: fused or an error; 2: always tap + reduce."""
+        L.check(self._lib, self._lib.bnm_ctx_set_profile_mode(self._h, mode), "bnm_ctx_set_profile_mode")
+
+    def profile_device(self, images, counters, labels=None, cls=None, stream=None):
+        """Classify and profile on the GPU, asynchronous on torch's current stream (or `stream`).  images: torch.int8 [n,256] or
+        torch.float32 [n,256] cuda tensor (floats are quantised as quantize_device does); counters: int64 cuda tensor of
+        profile_words() elements that the call ADDS to (zero it once); labels: int32 [n] or None; cls: int32 [n] (receives the
+        class ids) or None."""
+        import torch
+        n = images.shape[0]
+        assert images.is_cuda and images.is_contiguous() and images.dtype in (torch.int8, torch.float32)
+        assert counters.is_cuda and counters.is_contiguous() and counters.element_size() == 8
+        assert counters.numel() >= self.profile_words()
+        if labels is not None:
+            assert labels.is_cuda and labels.is_contiguous() and labels.dtype == torch.int32 and labels.numel() >= n
+        if cls is not None:
+            assert cls.is_cuda and cls.is_contiguous() and cls.element_size() == 4 and cls.numel() >= n
+        s = stream if stream is not None else torch.cuda.current_stream(images.device)
+        fn = self._lib.bnm_infer_device_profiled if images.dtype == torch.int8 else self._lib.bnm_infer_float_device_profiled
+        L.check(self._lib, fn(self._h, images.data_ptr(), n, cls.data_ptr() if cls is not None else None,
+                              labels.data_ptr() if labels is not None else None, counters.data_ptr(), s.cuda_stream),
+                fn.__name__)
+        return counters
+
+    def profile(self, images, labels=None, batch=1 << 20):
+        """Host images (int8 [n,256], or float32 [n,256] quantised on the GPU) -> ActivationProfile.  Only the counters come back."""
+        import torch
+        from .profile import ActivationProfile
+        x = np.asarray(images)
+        x = np.ascontiguousarray(x, dtype=np.int8 if x.dtype == np.int8 else np.float32).reshape(-1, 256)
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        dev = torch.device("cuda", self._lib.bnm_ctx_device(self._h))
+        counters = torch.zeros(self.profile_words(), dtype=torch.int64, device=dev)
+        for s in range(0, len(x), batch):
+            xb = torch.from_numpy(x[s:s + batch]).to(dev)
+            lb = None if lab is None else torch.from_numpy(lab[s:s + batch]).to(dev)
+            self.profile_device(xb, counters, labels=lb)
+        return ActivationProfile(self.model, counters.cpu().numpy())
+
     def quantize_device(self, x, out=None, stream=None):
         """float32 cuda tensor [n,256] -> int8 [n,256] on the GPU with the reference's input quantisation
         (test_inference.py:140-141), bit-identical to harness.quantize_input."""

@@ -282,6 +282,43 @@ BNM_API int bnm_ctx_set_float_mode(bnm_ctx *c, int mode, int groups);
 BNM_API int bnm_ctx_float_nonfinite(bnm_ctx *c, uint64_t *count);
 BNM_API int bnm_ctx_float_fused(const bnm_ctx *c);      /* 1: float calls of this context run one kernel now (CNN: those that take the one-kernel form); 0: two kernels */
 
+/* ---- activation profiles -----------------------------------------------------------------------
+ * Exact integer statistics of the engine's int8 activations, plus prediction and confusion counts, accumulated on the GPU in the
+ * pass that classifies; the host reads back only the counters.  A PROFILED LAYER is one whose ReLUNorm output feeds another layer:
+ * a CNN's front end (its 4*C features, feature index 4c + p as BitNetMCU_MNIST_dll.c:66-77 writes them), then every FC layer but
+ * the classifier, in schedule order.  The counters are uint64 words, in this order:
+ *     for each profiled layer l, width W_l:
+ *         active[l][W_l]   images whose activation j of layer l is > 0
+ *         sum[l][W_l]      sum over images of activation j (each 0..127)
+ *         hist[l][128]     activations of layer l equal to v, v = 0..127 (each row sums to images * W_l)
+ *     pred[n_classes]                    images classified as c (the class id the call returns)
+ *     confusion[n_classes][n_classes]    row = label, column = prediction (labelled calls only)
+ *     labelled                           images of labelled calls
+ *     label_out_of_range                 ... whose label is not in [0, n_classes): counted here, not in confusion
+ *     images                             images of all calls
+ * Calls ADD to the counters: the caller zeroes them once and may accumulate any number of calls, on any streams.
+ * Returns the number of words; *n_layers (nullable) receives the profiled layer count and widths (nullable; room for
+ * bnm_model_num_layers(m) entries) their widths.  CPU only. */
+BNM_API uint64_t bnm_model_profile_words(const bnm_model *m, uint32_t *n_layers, uint32_t *widths);
+/* bnm_infer_device plus the profile: d_images int8 [n][256] (16-byte aligned); d_cls uint32 [n] or NULL (the ids are then not
+ * kept), written with the ids bnm_infer_device returns; d_labels int32 [n] or NULL; d_counters bnm_model_profile_words() uint64
+ * words (8-byte aligned).  Asynchronous on `stream`, no host synchronisation.  FC models whose layers are at most 128 wide and
+ * that have at most 64 classes run ONE kernel, the profiling variant of the generic fused kernel (launches of up to 2^22 images).
+ * Every other model runs, per chunk of up to 2^20 images, the layer-wise path with its activation tap into per-stream scratch and a
+ * reduction kernel that adds the chunk's statistics to the counters; that form takes models of up to 16 profiled layers
+ * (BNM_EUNSUPPORTED beyond).  The scratch rules of bnm_infer_device hold: after one eager call of at least the same size on the
+ * capturing stream, a call may be captured into a HIP graph and replayed. */
+BNM_API int bnm_infer_device_profiled(bnm_ctx *c, const int8_t *d_images, uint64_t n, uint32_t *d_cls, const int32_t *d_labels,
+                                      uint64_t *d_counters, void *stream);
+/* The same for float32 images [n][256] (16-byte aligned): quantised first (bnm_quantize_input_device's arithmetic; an image holding a
+ * NaN or an infinity becomes the all-zero image and is counted in bnm_ctx_float_nonfinite, as by bnm_infer_float_device). */
+BNM_API int bnm_infer_float_device_profiled(bnm_ctx *c, const float *d_x, uint64_t n, uint32_t *d_cls, const int32_t *d_labels,
+                                            uint64_t *d_counters, void *stream);
+/* How profiled calls run: 0 (default) the fused profiling kernel where it serves the model, else tap + reduce; 1 fused, or
+ * BNM_EUNSUPPORTED here for a model it does not serve; 2 always tap + reduce (A/B checks).  bnm_ctx_last_kernel names what a
+ * profiled call ran.  Results are identical in every mode. */
+BNM_API int bnm_ctx_set_profile_mode(bnm_ctx *c, int mode);
+
 /* ---- several FC models over one image batch ---------------------------------------------------
  * A bnm_multi holds 1 .. 16 FC models (256-byte inputs, a fused MFMA path; they may differ in depth, widths, codecs and class
  * counts, and the same model may appear twice) on one GPU.  One call runs all of them over the same images: the planner groups the
